@@ -12,11 +12,20 @@ Precision (--precision, default bf16x3): the GEMMs run either on the exact
 f32 MFMA ("fp32") or as exact 3-way bf16 splits with six bf16 MFMA products
 per fp32 product and fp32 accumulation ("bf16x3": fp32-class accuracy,
 nerfhip.h nerfhip_precision); everything else is fp32 in both.  Both are held
-to the same per-fit parity bar (cos_delta_vs_ref).  With --also-fp32 (default
-on at N=1) the line also carries the fp32 sweep, timed under the same
-protocol (one warm-up, three timed sweeps).
+to the same per-fit parity bar (cos_delta_vs_ref).
 
-Also reported (rank 0):
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, runs W untimed
+and K timed steps and prints the result line: value, ms_per_step (the
+milliseconds of one timed step) and the run's configuration.  With
+`--dump-outputs DIR` it also writes what the last timed step computed for every
+fit as DIR/<name>.npy (float32, one row per fit in sweep order; dump_record):
+the inputs are the seed-0 sweep in every run, so two builds compare output for
+output.  Everything below is measured only with `--full`, which also brackets
+the step kernels of every 4th epoch of the timed steps with hipEvents.  With
+--also-fp32 (default on at N=1) the --full line also carries the fp32 sweep,
+timed under the same protocol (one warm-up, three timed sweeps).
+
+Also reported with --full (rank 0):
   roofline      the dominant kernel's algorithmic TFLOP/s against the
                 matrix-core peak of its arithmetic (157.3 TFLOP/s f32 MFMA, or
                 2.5 PFLOP/s bf16 dense / 6 products = 416.7 TFLOP/s
@@ -330,6 +339,50 @@ def fp32_sweep(specs, epochs, device, plan, ref_cos, n_total, warmup: int = 1,
     return out
 
 
+DUMP_COLS = 8192    # longest per-fit vector written whole by --dump-outputs
+DUMP_SEED = 0
+
+
+def dump_cols(n: int) -> np.ndarray:
+    """Which entries of a per-fit vector of length n --dump-outputs keeps: all
+    of them up to DUMP_COLS, else a sorted sample of DUMP_COLS drawn without
+    replacement from a generator seeded by (DUMP_SEED, n) — the same entries
+    in every run and every build, so two dumps compare entry for entry."""
+    if n <= DUMP_COLS:
+        return np.arange(n)
+    return np.sort(np.random.default_rng([DUMP_SEED, n]).choice(n, DUMP_COLS, replace=False))
+
+
+def dump_record(o) -> dict:
+    """What a caller of the timed path receives for one fit (engine.FitOutput),
+    as float32 vectors: the trained parameters, every epoch's loss, the final
+    per-position cosine and MSE, the final MSE and the target's normalisation
+    statistics.  Vectors longer than DUMP_COLS are sampled (dump_cols), which
+    bounds the 280-fit dump at 4 x 280 x DUMP_COLS floats (37 MB) plus the
+    short ones."""
+    vec = {"params": o.params.detach().cpu().numpy(), "losses": np.asarray(o.losses),
+           "row_cos": o.row_cos, "row_mse": o.row_mse, "final_mse": np.array([o.final_mse]),
+           "target_mean": o.target_mean.numpy(), "target_std": o.target_std.numpy()}
+    out = {}
+    for name, v in vec.items():
+        v = np.asarray(v, dtype=np.float32).reshape(-1)
+        out[name] = v[dump_cols(v.size)]
+    return out
+
+
+def write_dump(out_dir: Path, records: dict) -> None:
+    """DIR/<name>.npy, one row per fit in sweep order; rows of fits with fewer
+    entries (the smaller architectures' parameters) are padded with zeros."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    order = sorted(records)
+    for name in records[order[0]]:
+        rows = [records[i][name] for i in order]
+        a = np.zeros((len(rows), max(r.size for r in rows)), dtype=np.float32)
+        for k, r in enumerate(rows):
+            a[k, :r.size] = r
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def dry_run(args, world: int, rank: int) -> None:
     """The multi-rank protocol of main() with the device work left out: every
     rank takes its LPT share of the sweep's FLOP costs, 'trains' nothing, and
@@ -368,13 +421,24 @@ def main() -> None:
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--precision", default="bf16x3", choices=["fp32", "bf16x3"])
     ap.add_argument("--also-fp32", dest="also_fp32", action="store_true", default=None,
-                    help="also time one fp32 sweep (default: on at N=1 with bf16x3)")
+                    help="with --full: also time the fp32 sweep (default: on at N=1 with bf16x3)")
     ap.add_argument("--no-also-fp32", dest="also_fp32", action="store_false")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the fit_kv_cache wall-clock leg")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="with --full: skip the fit_kv_cache wall-clock leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel timing and roofline (with the isolated "
+                         "kernel leg), parity against the reference's sweep, and at N=1 the fp32 "
+                         "sweep, the fit_kv_cache wall clock and the CPU baseline (each with its "
+                         "own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed for every fit "
+                         "as DIR/<name>.npy (float32; see dump_record)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher self-test without a GPU: rank spawn, gloo group, LPT shares, "
                          "barrier, max-over-ranks and record gather, no device work")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     from nerf_attention import farm
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -421,7 +485,7 @@ def main() -> None:
     t0 = time.perf_counter()
     kt = [[0.0, 0.0, 0] for _ in job.groups]       # per group: rows ms, params ms, launches
     for _ in range(args.steps):
-        job.launch(timed=not args.no_kernel_timing)
+        job.launch(timed=args.full and not args.no_kernel_timing)
         job.wait()
         for acc, t in zip(kt, job.timing or []):
             acc[0] += t.rows_ms
@@ -432,10 +496,16 @@ def main() -> None:
     elapsed = time.perf_counter() - t0
     t_max = farm.max_over_ranks(elapsed)
 
-    # per-fit results for the parity summary (host-side gather; not timed)
-    outs = job.outputs()
+    # per-fit results of the last timed step (host-side gather; not timed):
+    # for --dump-outputs and for the parity summary of --full
+    outs = job.outputs() if (args.full or args.dump_outputs) else []
+    if args.dump_outputs:
+        dumped = farm.gather_records({mine[k]: dump_record(o) for k, o in enumerate(outs)})
+        if rank == 0:
+            write_dump(Path(args.dump_outputs), dumped)
+            progress(f"outputs of {len(dumped)} fits written to {args.dump_outputs}")
     my_cos = {mine[k]: float(torch.from_numpy(o.row_cos).mean()) for k, o in enumerate(outs)}
-    all_cos = farm.gather_records(my_cos)
+    all_cos = farm.gather_records(my_cos) if args.full else {}
 
     if rank == 0:
         value = n_total * args.steps / t_max
@@ -558,7 +628,7 @@ def main() -> None:
                     "job_frac": round(job_tf / peak, 4),
                     "job_frac_of_f32_mfma_peak": round(job_tf / FP32_MFMA_PEAK_TFLOPS, 4)}
         parity = None
-        if GOLDEN_SWEEP.exists() and args.epochs == 2000 and args.seq_len == 2048:
+        if args.full and GOLDEN_SWEEP.exists() and args.epochs == 2000 and args.seq_len == 2048:
             ref = json.loads(GOLDEN_SWEEP.read_text())["records"]
             names = [p[0] for p in plan]
             byname = {r["name"]: r["final_cosine_mean"] for r in ref}
@@ -582,19 +652,21 @@ def main() -> None:
                        "parallelism": f"fit-farm over {world} GPU(s), "
                                       f"{farm.auto_partition(world) if world > 1 else 'one'} "
                                       f"partition by FLOPs, gloo control only"},
+            "full": args.full,
             "roofline": roof,
             "cos_delta_vs_ref": parity,
         }
+        legs = args.full and world == 1
         also = args.also_fp32 if args.also_fp32 is not None else args.precision != "fp32"
-        if world == 1 and also:
+        if legs and also:
             progress("fp32 sweep")
             line["fp32_mfma"] = fp32_sweep([specs[i] for i in mine], args.epochs, local, plan,
                                            all_cos if parity else None, n_total)
-        if world == 1 and not args.no_e2e:
+        if legs and not args.no_e2e:
             progress("e2e fit_kv_cache")
             line["e2e_fit_kv_cache"] = e2e_fit_kv_cache(args.seq_len, args.epochs, args.precision)
             line["e2e_fits_per_s"] = line["e2e_fit_kv_cache"]["fits_per_s"]
-        if world == 1 and not args.no_cpu_baseline:
+        if legs and not args.no_cpu_baseline:
             progress("cpu baseline")
             line["cpu_baseline"] = cpu_baseline(args.seq_len, args.cpu_sample_epochs)
         print(json.dumps(line), flush=True)

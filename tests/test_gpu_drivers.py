@@ -64,11 +64,17 @@ def test_sweep_280_vs_reference(gpu, golden_dir, sweep):
     # trained the fit (siren.py:96,117's loop wall clock); the longest group is
     # the sweep's training time
     assert all(o.train_time_seconds == o.group_seconds > 0 for o in outs)
-    groups = {}
-    for o in outs:
-        groups.setdefault((o.group_seconds, o.plan["rows_workgroups"]), []).append(o)
-    assert len(groups) >= 7                                    # one interval per group / chunk
-    for members in groups.values():                            # FLOP shares split each interval
+    # one interval per group / chunk of the engine's plan.  (The groups are
+    # told apart by their members, not by the interval: two equal chunks can
+    # measure the same interval to the last bit.)
+    groups = [[outs[i] for i in m] for _d, m in engine.plan_groups(specs, 0)]
+    assert len(groups) >= 7 and sum(len(members) for members in groups) == 280
+    # per group, not one interval for the job: the 40 tiny fits need a small
+    # fraction of the 40 large fits' time
+    assert len({members[0].group_seconds for members in groups}) >= 2
+    for members in groups:
+        assert len({(o.group_seconds, o.plan["rows_workgroups"]) for o in members}) == 1
+        # FLOP shares split each interval
         assert abs(sum(o.flop_share_seconds for o in members) / members[0].group_seconds - 1) <= 1e-6
 
 

@@ -256,3 +256,42 @@ def test_bench_pmc_figures_only_for_the_measured_library(tmp_path):
     # the committed round-5 summary names the in-tree library when it is current
     real = json.loads((root / "profiles/r05/pmc_isolated_rows256.json").read_text())
     assert all("lib_sha16" in v for v in real.values())
+
+
+def test_bench_dump_outputs_layout(tmp_path):
+    """bench.py --dump-outputs: one float32 row per fit in sweep order, short
+    vectors whole (smaller fits zero-padded), vectors over DUMP_COLS entries as
+    the same sorted sample in every call, and a bounded total size."""
+    import sys
+    from pathlib import Path
+    from types import SimpleNamespace
+    root = Path(__file__).resolve().parent.parent
+    sys.path.insert(0, str(root))
+    import bench
+    assert np.array_equal(bench.dump_cols(100), np.arange(100))
+    cols = bench.dump_cols(3 * bench.DUMP_COLS)
+    assert cols.size == bench.DUMP_COLS and np.all(np.diff(cols) > 0) and cols[-1] < 3 * bench.DUMP_COLS
+    assert np.array_equal(cols, bench.dump_cols(3 * bench.DUMP_COLS))
+
+    def fit(k, P):
+        return SimpleNamespace(params=torch.arange(P, dtype=torch.float32) + k,
+                               losses=[1.0 / (e + 1 + k) for e in range(50)],
+                               row_cos=np.full(64, 0.5 + k, np.float32),
+                               row_mse=np.full(64, 0.25, np.float32), final_mse=0.125 * (k + 1),
+                               target_mean=torch.zeros(1, 128), target_std=torch.ones(1, 128))
+
+    big = 3 * bench.DUMP_COLS
+    recs = {2: bench.dump_record(fit(2, big)), 0: bench.dump_record(fit(0, 100)),
+            1: bench.dump_record(fit(1, big))}
+    bench.write_dump(tmp_path / "d", recs)
+    got = {f.stem: np.load(f) for f in (tmp_path / "d").glob("*.npy")}
+    assert set(got) == {"params", "losses", "row_cos", "row_mse", "final_mse", "target_mean",
+                        "target_std"}
+    assert all(a.dtype == np.float32 and a.shape[0] == 3 for a in got.values())
+    assert got["params"].shape == (3, bench.DUMP_COLS)
+    assert np.array_equal(got["params"][0, :100], np.arange(100)) and not got["params"][0, 100:].any()
+    assert np.array_equal(got["params"][1], cols + 1) and np.array_equal(got["params"][2], cols + 2)
+    assert got["losses"].shape == (3, 50) and got["final_mse"][:, 0].tolist() == [0.125, 0.25, 0.375]
+    assert got["row_cos"][:, 0].tolist() == [0.5, 1.5, 2.5]
+    # the 280-fit sweep: at most four sampled vectors and three short ones per fit
+    assert 280 * 4 * (4 * bench.DUMP_COLS + 2 * 128 + 1) <= 64e6

@@ -8,7 +8,7 @@ tag="${1:-x3}"; prec="${2:-bf16x3}"
 out="$R/gpurun_out/prof_$tag"
 mkdir -p "$out"
 export TMPDIR=/tmp
-B="$R/bench.py --epochs 200 --no-cpu-baseline --no-also-fp32 --no-e2e --precision $prec"
+B="$R/bench.py --full --epochs 200 --no-cpu-baseline --no-also-fp32 --no-e2e --precision $prec"
 cd /tmp
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$out/trace" -o run --output-format csv -- python3 $B > "$out/trace.log" 2>&1 || { echo "trace rc=$?"; tail "$out/trace.log"; exit 1; }
 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d "$out/fetch" -o run --output-format csv -- python3 $B > "$out/fetch.log" 2>&1 || { echo "fetch rc=$?"; tail "$out/fetch.log"; exit 1; }
