@@ -882,6 +882,27 @@ __device__ __forceinline__ void gemm_phase_x3(const uint16_t* __restrict__ src, 
   auto lgkm_wait = [](S8& r) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r.h), "+v"(r.m), "+v"(r.l));
   };
+  // the same, leaving the N LDS reads issued after r's in flight (LDS returns
+  // in order; any other lgkm operation in between only makes r's reads older)
+  auto lgkm_wait_n = [](S8& r, auto nc) {
+    asm volatile("s_waitcnt lgkmcnt(%3)"
+                 : "+v"(r.h), "+v"(r.m), "+v"(r.l)
+                 : "n"(decltype(nc)::value));
+  };
+  // AHEAD2: fragments are read two k-steps ahead inside a sub-chunk, each
+  // retired by a wait counted for exactly the reads issued after it.  On for
+  // one wave per SIMD (PIN, W = 512), where no second wave covers a fragment's
+  // LDS round trip and registers are free (the isolated large x 40 launch
+  // measured about 5 % faster).  Off at two waves per SIMD: at W = 256 the
+  // third fragment set's 12 VGPRs go to scratch (120 -> 200 B per lane, 33 ->
+  // 61 spilled registers) and the deep x 40 launch measured 14 % slower
+  // (DESIGN.md §14).
+  constexpr bool AHEAD2 = PIN;
+#if NERFHIP_X2P(4)
+  constexpr int NRD = 2;   // ds_read_b128 per fragment
+#else
+  constexpr int NRD = 3;
+#endif
   // Retire sub-chunk u+1's DMA, which is older than every vm op issued in
   // iteration u: [flush stores][pre loads][DMA(u+2)].  Those may stay in flight,
   // so the wait leaves exactly their count outstanding (NST / NLD are the exact
@@ -920,10 +941,17 @@ __device__ __forceinline__ void gemm_phase_x3(const uint16_t* __restrict__ src, 
 #endif
     __builtin_amdgcn_sched_barrier(0);
     const unsigned long long t_d1 = MEMTIME();
+    S8 a_n1 = a_cur;   // AHEAD2: the fragment after the next, in flight
+    if constexpr (AHEAD2 && KT > 1) a_n1 = aread(uc, std::integral_constant<int, 1>{});
     static_for<0, KT>([&](auto ktc) {
       constexpr int kt = decltype(ktc)::value;
       S8 a_nxt = a_cur;
-      if constexpr (kt + 1 < KT) a_nxt = aread(uc, std::integral_constant<int, kt + 1>{});
+      if constexpr (AHEAD2) {
+        a_nxt = a_n1;   // fragment kt + 1, issued a k-step ago
+        if constexpr (kt + 2 < KT) a_n1 = aread(uc, std::integral_constant<int, kt + 2>{});
+      } else if constexpr (kt + 1 < KT) {
+        a_nxt = aread(uc, std::integral_constant<int, kt + 1>{});
+      }
       mfma16x3(a_cur, b[hh * KT + kt], hi, lo);
       if constexpr (hh == 0 && J > 0) {
 #pragma unroll
@@ -940,7 +968,9 @@ __device__ __forceinline__ void gemm_phase_x3(const uint16_t* __restrict__ src, 
       // at one wave per SIMD pinning measured 2.5 % faster (W = 512,
       // profiles/r02/ab_pin_lgkm.log).
       if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
-      if constexpr (kt + 1 < KT) lgkm_wait(a_nxt);
+      // AHEAD2: fragment kt + 2's NRD reads were issued after kt + 1's and stay in flight
+      if constexpr (AHEAD2 && kt + 2 < KT) lgkm_wait_n(a_nxt, std::integral_constant<int, NRD>{});
+      else if constexpr (kt + 1 < KT) lgkm_wait(a_nxt);
       __builtin_amdgcn_sched_barrier(0);
       a_cur = a_nxt;
     });
